@@ -11,13 +11,16 @@ Default workload = config C2 (stage2_vq.yaml model with num
 N=64 latent tokens), the configuration BASELINE.json's metric is quoted on.  A "step" = one full training step on a
 per-rank batch of 256 synthetic curve tensors [256, 64, 6] already resident in HBM: forward (dropout 0.1 active) +
 24-term loss + backward + RCCL all-reduce (N>1) + global-norm clip + AdamW + EMA codebook refresh, all fp32.
-Prints ONE JSON line (rank 0) with the whole-job samples/s, the roofline of the dominant kernel (the fp32-MFMA GEMM
-instantiation with the largest summed time, measured live with HIP events on the launch stream) and a CPU baseline
-(the oracle timed on the host cores; it is imported only inside that leg).
+Prints ONE JSON line (rank 0) with the whole-job samples/s and ms_per_step.  With --full it also measures the roofline of
+the dominant kernel (the GEMM instantiation with the largest summed time, measured live with HIP events on the launch stream
+over two extra eager steps) and a CPU baseline (the oracle timed on the host cores; it is imported only inside that leg);
+a plain run does neither and reports both as null.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_step_outputs).
 
 Other BASELINE shapes, for profiling (not the judged bench line):   --workload c4 | c5 | stage2
 The real-data path end to end (ragged lengths -> DataLoader -> pad_collate -> bucketed step):   --workload realdata
 The quantizer alone at SURVEY 8d's image-derived shapes (one JSON line per shape):   --vq-only
+(--full adds the quantizer's roofline and CPU baseline there, and the fixed-shape comparison to realdata)
 """
 import argparse
 import json
@@ -50,6 +53,7 @@ WORKLOADS = {
                    over=dict()),
 }
 VQ_SHAPES = [(65536, 512, 64), (262144, 8192, 256)]     # R = B*16*16 rows of the upstream image VQ-VAE
+DUMP_SAMPLE = 1 << 21                                   # positions sampled from the weights / gradients: 8 MB of float32 each
 
 
 def setup(workload):
@@ -105,6 +109,26 @@ def cpu_baseline(mp, weights, hp, B_cpu=256, L=64, steps=2):
             "sample": f"oracle train step (dropout 0.1, AdamW+clip), B={B_cpu} L={L}, {steps} timed steps after 1 warm-up"}
 
 
+def dump_step_outputs(model, eng, out_dir):
+    """--dump-outputs: what the last training step handed its caller, as float32 .npy files -- `metrics` (the vector
+    train_step returns, engine.METRIC_KEYS order), `params` / `grads` (the updated weights and the step's gradients,
+    concatenated in named_parameters order; above DUMP_SAMPLE elements a fixed seeded sample of positions, the same in
+    every run of the same model) and the quantizer's buffers (codebook, EMA statistics) whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    named = list(model.named_parameters())
+    w = torch.cat([p.detach().reshape(-1) for _, p in named])
+    g = torch.cat([eng.G[n].reshape(-1) for n, _ in named])
+    if w.numel() > DUMP_SAMPLE:
+        pos = np.unique(np.random.default_rng(1234).integers(0, w.numel(), DUMP_SAMPLE))
+        pos = torch.from_numpy(pos).to(w.device)
+        w, g = w[pos], g[pos]
+    arrays = {"metrics": eng.metrics, "params": w, "grads": g}
+    arrays.update({n: b for n, b in model.named_buffers() if n.startswith("quantizer.") and b.is_floating_point()})
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def pmc_traffic(kernel_name):
     """HBM bytes per launch of `kernel_name` from the newest committed rocprofv3 --pmc summary under profiles/ (collected
     in separate passes and corrected as MI355X_MICROARCH.md prescribes; see profiles/README.md), or None."""
@@ -148,6 +172,17 @@ def bench_vq_only(args, dev):
             step()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
+        out = {"metric": "VectorQuantizerEMA.forward rows/sec (nearest + gather + EMA update + usage stats)",
+               "value": round(R * args.steps / el, 1), "unit": "rows/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": round(el / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+               "dtype": "f32", "gemm_arithmetic": ("bf16x3 exact split (6 products, fp32 accumulate)" if args.gemm == "x3"
+                                                   else "native fp32 MFMA"),
+               "data": "synthetic",
+               "config": {"workload": f"vq-only R={R} K={K} D={D} (SURVEY.md 8d image-derived shape), fresh centroid-initialised table"},
+               "roofline": None, "cpu_baseline": None}
+        if not args.full:
+            print(json.dumps(out), flush=True)
+            continue
         n, t, f = L.vq_profile(lambda: [step() for _ in range(3)])
         # which score kernel ran (csrc/vq.hip dispatch): D = 64 / 128 / 256 -> the split-operand kernel on the bf16 pipes
         # (6 bf16 MFMA products per fp32 product) unless vqh_vq_set_flags bit 1 asks for the fp32 MFMA form
@@ -187,15 +222,7 @@ def bench_vq_only(args, dev):
             dtc = (time.time() - tc) / reps
             cpu = {"value": round(Rc / dtc, 1), "unit": "rows/s", "cores": ncores, "kind": "port",
                    "sample": f"oracle VectorQuantizerEMA.forward (train mode), R={Rc} of {R} rows, {reps} timed calls"}
-        out = {"metric": "VectorQuantizerEMA.forward rows/sec (nearest + gather + EMA update + usage stats)",
-               "value": round(R * args.steps / el, 1), "unit": "rows/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(el / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "f32", "gemm_arithmetic": ("bf16x3 exact split (6 products, fp32 accumulate)" if args.gemm == "x3"
-                                                   else "native fp32 MFMA"),
-               "data": "synthetic",
-               "config": {"workload": f"vq-only R={R} K={K} D={D} (SURVEY.md 8d image-derived shape), fresh centroid-initialised table"},
-               "roofline": vq_roof,
-               "cpu_baseline": cpu}
+        out.update(roofline=vq_roof, cpu_baseline=cpu)
         print(json.dumps(out), flush=True)
 
 
@@ -239,19 +266,25 @@ def bench_realdata(args, dev):
     el = time.perf_counter() - t0
     n_timed = len(shapes) - warm
     loss_end = float(eng.metrics[0])
-    # the same engine on one resident batch of the dominant bucket shape
-    Lb = max(set(b for _, b in shapes[warm:]), key=[b for _, b in shapes[warm:]].count)
-    from dataset import synthetic_curve_batch
-    x, mask = (t.to(dev) for t in synthetic_curve_batch(B, Lb, 4321, ragged=True, min_len=Lb // 2))
-    w, lr, wd, clip = exp.loss_weights(), exp.lr_policy.current()[0], exp.weight_decay, exp.trainer.gradient_clip_val
-    for _ in range(3):
-        eng.train_step(x, mask, w, lr, wd, clip)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(n_timed):
-        eng.train_step(x, mask, w, lr, wd, clip)
-    torch.cuda.synchronize()
-    el_fixed = time.perf_counter() - t1
+    if args.dump_outputs:
+        dump_step_outputs(exp.model, eng, args.dump_outputs)
+    fixed = None
+    if args.full:
+        # the same engine on one resident batch of the dominant bucket shape
+        Lb = max(set(b for _, b in shapes[warm:]), key=[b for _, b in shapes[warm:]].count)
+        from dataset import synthetic_curve_batch
+        x, mask = (t.to(dev) for t in synthetic_curve_batch(B, Lb, 4321, ragged=True, min_len=Lb // 2))
+        w, lr, wd, clip = exp.loss_weights(), exp.lr_policy.current()[0], exp.weight_decay, exp.trainer.gradient_clip_val
+        for _ in range(3):
+            eng.train_step(x, mask, w, lr, wd, clip)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(n_timed):
+            eng.train_step(x, mask, w, lr, wd, clip)
+        torch.cuda.synchronize()
+        el_fixed = time.perf_counter() - t1
+        fixed = {"value": round(B * n_timed / el_fixed, 2), "ms_per_step": round(el_fixed / n_timed * 1e3, 3),
+                 "what": f"same engine, one device-resident ragged batch [B={B}, L={Lb}], graph replay"}
     out = {"metric": "train images/sec, real-data path (ragged curves -> DataLoader -> pad_collate -> bucketed fused step)",
            "value": round(B * n_timed / el, 2), "unit": "images/s", "n_gpus": 1, "steps": n_timed, "warmup": warm,
            "ms_per_step": round(el / n_timed * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -261,9 +294,7 @@ def bench_realdata(args, dev):
                       "raw_L_max_seen": sorted(set(a for a, _ in shapes)), "buckets_seen": sorted(set(b for _, b in shapes)),
                       "arenas": len(eng.arenas) - 1,
                       "step_modes_timed": {mo: modes[warm:].count(mo) for mo in sorted(set(modes[warm:]))}},
-           "fixed_shape": {"value": round(B * n_timed / el_fixed, 2), "ms_per_step": round(el_fixed / n_timed * 1e3, 3),
-                           "what": f"same engine, one device-resident ragged batch [B={B}, L={Lb}], graph replay"},
-           "realdata_over_fixed": round(el_fixed / el, 4), "loss": round(loss_end, 5)}
+           "fixed_shape": fixed, "realdata_over_fixed": round(el_fixed / el, 4) if fixed else None, "loss": round(loss_end, 5)}
     print(json.dumps(out), flush=True)
 
 
@@ -281,8 +312,15 @@ def main():
     ap.add_argument("--gemm", choices=["x3", "native"], default="x3",
                     help="large GEMM tiles: x3 = bf16 matrix pipes fed by an exact 3-way split of the fp32 operands (default); "
                          "native = v_mfma_f32_32x32x2_f32")
-    ap.add_argument("--no-kernel-profile", action="store_true", help="skip the two eager HIP-event-timed steps (rocprofv3 runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the dominant kernel's roofline (two extra eager "
+                         "steps), the CPU baseline, the fixed-shape comparison of --workload realdata")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="with --full: skip the two eager HIP-event-timed steps (rocprofv3 runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32, under 64 MB)")
     args = ap.parse_args()
+    if args.dump_outputs and args.vq_only:
+        ap.error("--dump-outputs: the --vq-only bench writes no outputs")
 
     # --gpus N without a launcher: start the N ranks ourselves, as CHILD processes, before anything touches the GPU
     # (a process that has initialised HIP is never re-exec'ed); rank 0 of the children prints the JSON line.
@@ -352,11 +390,13 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = B * world * args.steps / elapsed
     metrics = eng.metrics_dict(weights)
+    if args.dump_outputs and rank == 0:
+        dump_step_outputs(model, eng, args.dump_outputs)
 
     # ---- roofline of the dominant kernel: HIP events around every GEMM main-kernel launch of 2 eager steps, recorded
     # by the library on the launch stream and keyed by kernel instantiation (the names rocprofv3 prints) -------------
     roof = None
-    if not args.no_kernel_profile:
+    if args.full and not args.no_kernel_profile:
         def two_eager_steps():
             for _ in range(2):      # every rank runs them (they contain the collective); only rank 0 reports
                 eng.train_step(x, mask, weights, hp["lr"], hp["wd"], hp["clip"], use_graph=False)
@@ -392,7 +432,7 @@ def main():
                                    "achieved": round(value / world * wl["gflop"] / 1e3, 2)}}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(mp, weights, hp, B_cpu=min(B, 256), L=min(Lq, 64))
 
     if rank == 0:

@@ -26,9 +26,8 @@ published semantics:
 
 Parity pin: the reference has NO tests or golden vectors.  The pin is
 tests/golden/*.npz, produced by tests/golden/make_golden.py, which imports the real reference
-from /root/reference in the build container and records its inputs/outputs; tests/test_oracle.py
-checks this file against those fixtures (and, when /root/reference is present, against the live
-reference).  The state is a flat dict {reference state_dict key -> tensor}, so a reference
+and records its inputs/outputs; tests/test_oracle.py checks this file against those fixtures
+only.  The state is a flat dict {reference state_dict key -> tensor}, so a reference
 state_dict loads without renaming.
 """
 import math

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 stats() {   # name, bench args...
   local name="$1"; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$name" -- python3 "$R/bench.py" "$@" --no-cpu-baseline > "$OUT/stats_$name.log" 2>&1 || echo "stats $name failed"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$name" -- python3 "$R/bench.py" "$@" --full --no-cpu-baseline > "$OUT/stats_$name.log" 2>&1 || echo "stats $name failed"
   cp $(find "$OUT/stats_$name" -name "*kernel_stats.csv" | head -1) "$OUT/r03_${name}_kernel_stats_rocprofv3.csv" 2>/dev/null
   grep '^{' "$OUT/stats_$name.log" | tail -2 > "$OUT/r03_${name}_bench_line.json"
   rm -rf "$OUT/stats_$name"
@@ -20,7 +20,7 @@ stats() {   # name, bench args...
 }
 pmc() {     # name, counters, bench args...
   local name="$1" ctr="$2"; shift 2
-  rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d "$OUT/pmc_$name" -- python3 "$R/bench.py" "$@" --no-graph --no-cpu-baseline > "$OUT/pmc_$name.log" 2>&1 || echo "pmc $name failed"
+  rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d "$OUT/pmc_$name" -- python3 "$R/bench.py" "$@" --full --no-graph --no-cpu-baseline > "$OUT/pmc_$name.log" 2>&1 || echo "pmc $name failed"
   echo "[collect] pmc $name done"
 }
 if [ "$WHAT" = "c2" ]; then

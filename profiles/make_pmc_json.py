@@ -3,8 +3,8 @@
 /opt/skills/guides/MI355X_MICROARCH.md prescribes: FETCH_SIZE and WRITE_SIZE do not fit one pass):
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <out>/pmc_fetch -- python bench.py --steps 2 --warmup 3 --no-graph --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <out>/pmc_write -- python bench.py --steps 2 --warmup 3 --no-graph --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <out>/pmc_fetch -- python bench.py --steps 2 --warmup 3 --full --no-graph --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <out>/pmc_write -- python bench.py --steps 2 --warmup 3 --full --no-graph --no-cpu-baseline
     python profiles/make_pmc_json.py <out>/pmc_fetch <out>/pmc_write profiles/r01_c2_pmc_traffic.json
 
 Per kernel: average FETCH_SIZE / WRITE_SIZE (KB) per launch and hbm_bytes_per_launch_corrected = (2*FETCH + WRITE)*1024

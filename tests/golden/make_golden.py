@@ -490,6 +490,34 @@ def dataset_case(name="dataset"):
     print(f"[golden] {name}: CurveDataset on .npy dict / .npz / NaN file, shape errors")
 
 
+# ------------------------------------------------------------------------------------------
+# 7. forward of the whole model with dropout off on a seed none of the cases above uses (train mode, one step in):
+#    reconstructions and code indices, for tests/test_oracle.py::test_oracle_matches_live_reference_with_dropout_off
+# ------------------------------------------------------------------------------------------
+def forward_case(name, cfg_kw, state_seed, B, L, x_seed):
+    sd0 = G.model_state(cfg_kw, state_seed)
+    ref = RefVQVAE(**cfg_kw)
+    ref.load_state_dict(sd0, strict=True)
+    zero_dropout(ref)
+    ref.train()
+    ref.training_steps = 1
+    x, mask = G.curve_batch(B, L, x_seed, ragged=True)
+    with torch.no_grad():
+        r = ref(x, mask)
+    orc = O.OracleVQVAE({k: v.clone() for k, v in sd0.items()}, drop_scale=0.0, **cfg_kw)
+    orc.training_steps = 1
+    with torch.no_grad():
+        o = orc.forward(x, mask)
+    close(o[0], r[0], 2e-5, f"{name} recons")
+    assert torch.equal(o[2][2], r[2][2]), f"oracle != reference for {name} indices"
+    out = {"state_seed": state_seed, "B": B, "L": L, "x_seed": x_seed,
+           "x_sum": G.checksum(x), "mask_sum": G.checksum(mask.float()),
+           "state_sum": sum(G.checksum(v) for v in sd0.values()),
+           "recons": np_(r[0]), "indices": np_(r[2][2])}
+    np.savez_compressed(os.path.join(HERE, f"{name}.npz"), **out)
+    print(f"[golden] {name}: B={B} L={L} forward, dropout off")
+
+
 if __name__ == "__main__":
     only = set(sys.argv[1:])
     want = lambda n: (not only) or (n in only)
@@ -533,3 +561,5 @@ if __name__ == "__main__":
         init_case("init_small_vq_seed1265", G.SMALL_VQ, 1265)
         init_case("init_c2_seed1265", G.C2_MODEL, 1265)
         init_case("init_small_ae_seed7", G.SMALL_AE, 7)
+    if want("forward"):
+        forward_case("forward_small_vq_seed777", G.SMALL_VQ, 777, 3, 19, 778)

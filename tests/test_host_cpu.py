@@ -379,12 +379,13 @@ def test_get_epoch_stats_dict_matches_reference():
         assert q.get_epoch_stats()["n_positions"] == 0
 
 
-def test_devices_resolution_and_single_command_launch(tmp_path):
+def test_devices_resolution_and_single_command_launch(tmp_path, monkeypatch):
     """trainer_params.devices drives the rank count like Lightning's `devices: N, strategy: ddp` (reference run.py:191-218):
     `python run.py -c cfg` with devices: 2 starts 2 child ranks itself.  Without a GPU the children fail loudly -- which is
     the proof that they were started (the parent never touches the GPU)."""
     import subprocess
     import run as run_mod
+    monkeypatch.setenv("VQH_DIST_BACKEND", "gloo")      # ranks may share a device: no capping to the GPUs of this machine
     assert run_mod.resolve_devices({"devices": 1}) == 1
     assert run_mod.resolve_devices({"devices": [0, 1, 2]}) == 3
     assert run_mod.resolve_devices({"devices": "2"}) == 2

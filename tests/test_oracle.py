@@ -183,32 +183,19 @@ def test_oracle_state_dict_layout_matches_reference_keys():
         assert sum(int(np.prod(s)) for s in O.param_shapes(cfg).values()) == int(g["n_params"])
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference"), reason="reference tree absent (GPU box)")
 def test_oracle_matches_live_reference_with_dropout_off():
-    """Build container only: a fresh comparison against the imported reference on a new seed."""
-    import importlib.util
-    import warnings
-    warnings.filterwarnings("ignore")
-    # load the reference module under its own name: `models` may already be OUR package in this process
-    spec = importlib.util.spec_from_file_location("reference_vq_vae", "/root/reference/models/vq_vae.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    Ref = mod.VQVAE
+    """The whole forward on a seed none of the other fixtures uses, against the reference's outputs recorded by
+    make_golden.py (section 7: dropout forced off, train mode, one step in)."""
+    g = load_golden("forward_small_vq_seed777")
     cfg_kw = dict(G.SMALL_VQ)
-    sd0 = G.model_state(cfg_kw, 777)
-    ref = Ref(**cfg_kw)
-    ref.load_state_dict(sd0, strict=True)
-    for m in ref.modules():
-        if isinstance(m, torch.nn.Dropout):
-            m.p = 0.0
-        if isinstance(m, torch.nn.MultiheadAttention):
-            m.dropout = 0.0
-    ref.train()
-    ref.training_steps = 1
+    sd0 = G.model_state(cfg_kw, int(g["state_seed"]))
+    x, mask = G.curve_batch(int(g["B"]), int(g["L"]), int(g["x_seed"]), ragged=True)
+    assert abs(G.checksum(x) - float(g["x_sum"])) < 1e-6, "input RNG drift: regenerate fixtures"
+    assert abs(G.checksum(mask.float()) - float(g["mask_sum"])) < 1e-6, "mask RNG drift: regenerate fixtures"
+    assert abs(sum(G.checksum(v) for v in sd0.values()) - float(g["state_sum"])) < 1e-5, "weight RNG drift: regenerate fixtures"
     orc = O.OracleVQVAE({k: v.clone() for k, v in sd0.items()}, drop_scale=0.0, **cfg_kw)
     orc.training_steps = 1
-    x, mask = G.curve_batch(3, 19, 778, ragged=True)
     with torch.no_grad():
-        r, o = ref(x, mask), orc.forward(x, mask)
-    _close(o[0], r[0], 2e-5, "recons")
-    assert torch.equal(o[2][2], r[2][2])
+        o = orc.forward(x, mask)
+    _close(o[0], g["recons"], 2e-5, "recons")
+    assert torch.equal(o[2][2], torch.from_numpy(g["indices"]))
