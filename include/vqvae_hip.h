@@ -272,6 +272,37 @@ int vqh_grad_norm(const float* g, long long n, const float* hyper, float* norm_o
 int vqh_adamw_step(float* p, float* g, float* m, float* v, long long n, const float* hyper, const float* norm,
                    vqh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Validity screen of decoded curves: the reference's prior/filter_curves.py (bond_length_stats, bond_angle_stats,
+ * radius_of_gyration, self_collision_stats, segment_self_clash_count, beta_stats, beta_strand_and_sheet_stats and the
+ * accept / reject chain of its main) for a whole padded batch in one call.
+ *   curves  [B, Lmax, C] fp32 contiguous, C >= 3: xyz, then (C >= 6) three SS channels: one-hot, or logits when ss_logits != 0
+ *           (the kernel takes their argmax, first maximum on ties, like torch.argmax)
+ *   lengths [B] int32: valid prefix of each curve (clamped to 0..Lmax); positions beyond it are never read
+ *   params  HOST pointer, read during the call
+ *   ints    [B, 14] int32: length, reason, bond_num, bond_out, angle_num, angle_out, n_self_clash_pairs (ORDERED pairs: the
+ *           reference counts (i,j) and (j,i)), n_seg_clash_pairs (unordered), beta_total, beta_max_run, beta_in_sheet,
+ *           beta_strands_total, beta_strands_sheet, beta_strands_isolated
+ *           reason: 0 kept, 1 too short, 2 too long, 3 bond, 4 angle, 5 point collision, 6 segment clash, 7 SS rules
+ *           (the first failing check in the script's order; unlike the script every statistic is computed for every curve)
+ *   floats  [B, 12] fp32: bond mean, std, min, max, frac_out; angle mean, std, min, max, frac_out (degrees, angles with
+ *           |v1||v2| <= 1e-6 left out); rg; beta_sheet_fraction
+ *   keep_idx [B] int32: ascending indices of the curves with reason 0, at most max_curves of them (0 = no cap: the script's
+ *           `break`; `reason` of the curves beyond the cap is left as computed), then -1;  n_keep [1] int32: how many
+ * Lmax <= VQH_FILTER_MAX_LEN.  No host synchronisation: safe to capture into a hipGraph (params are baked into the capture).
+ * ------------------------------------------------------------------------------------------- */
+#define VQH_FILTER_MAX_LEN 2048
+typedef struct vqh_filter_params_t {
+    double bond_min_allowed, bond_max_allowed, bond_good_min, bond_good_max, bond_frac_out_max;
+    double angle_min_allowed, angle_max_allowed, angle_good_min, angle_good_max, angle_frac_out_max;
+    double min_pairwise_dist, seg_min_dist, sheet_min_dist, sheet_max_dist, ss_threshold, min_beta_sheet_fraction;
+    int min_length, max_length, neighbor_exclude, seg_neighbor_exclude, seg_num_samples;
+    int min_beta_run, min_beta_total, beta_channel, max_isolated_beta_strands, min_strand_len, max_curves;
+} vqh_filter_params_t;
+int vqh_curve_filter(const float* curves, int B, int Lmax, int C, const int* lengths, int ss_logits,
+                     const vqh_filter_params_t* params, int* ints, float* floats, int* keep_idx, int* n_keep,
+                     vqh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -602,6 +602,40 @@ class VQVAE(nn.Module):
         mask = torch.ones(num_samples, L_out, dtype=torch.bool, device=dev)
         return self.decode(z, mask=mask)
 
+    @torch.no_grad()
+    def sample_filtered(self, num_samples: int, device, out_len: Optional[int] = None, params=None, max_rounds: int = 8):
+        """sample -> validity screen on the GPU (vqvae_hip.curve_filter, the reference's prior/filter_curves.py rules with
+        the SS channels taken as logits) -> gather of the kept curves, repeated until num_samples curves are kept or
+        max_rounds rounds have run.  Returns (curves [n <= num_samples, L, 6] = xyz + SS one-hot of the argmax,
+        {"ints": [n, 14], "floats": [n, 12]} in the filter's column order).  One host read (n_keep) per round; no curve is
+        required to pass: with max_rounds exhausted the call returns what it has, possibly n = 0."""
+        from vqvae_hip import curve_filter as _F
+        params = copy.copy(params) if params is not None else _F.FilterParams()
+        L_out = out_len if out_len is not None else self.max_seq_len
+        kept, ints, floats, n = [], [], [], 0
+        for _ in range(int(max_rounds)):
+            if n >= num_samples:
+                break
+            rec = self.sample(num_samples, device, out_len=L_out)
+            params.max_curves = num_samples - n            # the screen itself caps what a round may add
+            res = _F.filter_curves(rec, params=params, ss_logits=True)
+            k = int(res.n_keep.item())
+            if k == 0:
+                continue
+            idx = res.keep_idx[:k].long()
+            sel = rec.index_select(0, idx)
+            ss = torch.nn.functional.one_hot(sel[..., 3:6].argmax(-1), 3).to(sel.dtype)
+            kept.append(torch.cat([sel[..., :3], ss], -1))
+            ints.append(res.ints.index_select(0, idx))
+            floats.append(res.floats.index_select(0, idx))
+            n += k
+        if not kept:
+            dev = self.quantizer.embedding.device
+            return (torch.empty(0, L_out, 6, device=dev),
+                    {"ints": torch.empty(0, len(_F.INT_COLUMNS), dtype=torch.int32, device=dev),
+                     "floats": torch.empty(0, len(_F.FLOAT_COLUMNS), device=dev)})
+        return torch.cat(kept), {"ints": torch.cat(ints), "floats": torch.cat(floats)}
+
 
 class _LossBridge(torch.autograd.Function):
     """Lets `loss_dict['loss'].backward()` (the Lightning-style call) trigger the HIP backward pass."""
