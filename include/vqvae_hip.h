@@ -303,6 +303,34 @@ int vqh_curve_filter(const float* curves, int B, int Lmax, int C, const int* len
                      const vqh_filter_params_t* params, int* ints, float* floats, int* keep_idx, int* n_keep,
                      vqh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Export of prior-training data: the device side of the reference's scripts/extract_code_indices.py (_ensure_batch_first_2d,
+ * compute_latent_geometry_for_sample) and scripts/decode_with_vqvae.py (indices_to_latent), for a whole batch per call.
+ * vqh_codes_pack
+ *   idx_level_major  what the quantizer returns: [Q, B, M] int64 global ids, level-major (models/vq_vae.py:245, :260); [B, M] for Q = 1
+ *   codes   [B, M*Q] int32 in the per-sample order t0_l0, t0_l1, ..., t0_l(Q-1), t1_l0, ...  (the [Q,B,M] -> [B,M,Q] permutation)
+ *   row_max [B] int32: the largest id of each row (the script's int16-or-int32 choice needs no second pass)
+ * vqh_codes_to_latent   the inverse of vqh_codes_pack followed by the codebook lookup
+ *   zq[b*M + t, :] = sum over q = 0..Q-1 of E[codes[b, t*Q + q], :], accumulated in fp32 in ascending q; E [K, D] with row stride lde;
+ *   zq [B*M, D] dense.  An id outside 0..K-1 contributes zeros and is counted in n_bad[0] (int32, set by every call); the
+ *   codebook is never read out of bounds.  16-byte loads / stores when D % 4 == 0, lde % 4 == 0 and E, zq are 16-byte aligned.
+ * vqh_latent_geometry
+ *   x       [B, Lmax, C] fp32 contiguous, 3 <= C <= 60: xyz, then C - 3 secondary-structure channels
+ *   lengths [B] int32: valid prefix of each curve (clamped to 0..Lmax); positions at or beyond it are never read
+ *   geo     [B, M*Q, G] fp32, G = C + 4; the M token rows are each written Q times (np.repeat).  Columns of a row:
+ *           0..2 segment centre; 3..5 unit direction (last - first) / (|last - first| + 1e-8), zeros for a one-point segment;
+ *           6..C+2 mean of each SS channel; C+3 radius sqrt(mean |p - centre|^2)
+ *   Segment t covers [bounds[t], bounds[t+1]) with bounds = np.linspace(0, L, M+1, dtype=int64), evaluated as numpy does:
+ *   (long long)((double)t * ((double)L / (double)M)) for t < M, L for t = M.  An empty segment becomes [start, min(L, start+1));
+ *   one that is still empty, and every row of a curve with L = 0, is all zeros.  Sums are taken in fp64 from the fp32 points.
+ * None of the three synchronises with the host: safe to capture into a hipGraph.
+ * ------------------------------------------------------------------------------------------- */
+int vqh_codes_pack(const long long* idx_level_major, int Q, int B, int M, int* codes, int* row_max, vqh_stream_t stream);
+int vqh_codes_to_latent(const int* codes, int B, int M, int Q, const float* E, int lde, int K, int D, float* zq, int* n_bad,
+                        vqh_stream_t stream);
+int vqh_latent_geometry(const float* x, int B, int Lmax, int C, const int* lengths, int M, int Q, float* geo,
+                        vqh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

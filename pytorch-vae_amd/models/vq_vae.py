@@ -602,6 +602,58 @@ class VQVAE(nn.Module):
         mask = torch.ones(num_samples, L_out, dtype=torch.bool, device=dev)
         return self.decode(z, mask=mask)
 
+    # ---- prior-training data: code indices out, code indices in (the reference's scripts/extract_code_indices.py and
+    # scripts/decode_with_vqvae.py) ---------------------------------------------------------------------------------
+    @torch.no_grad()
+    def encode_to_indices(self, x: Tensor, mask: Optional[Tensor] = None, return_row_max: bool = False):
+        """x [B, L, 6], mask [B, L] -> (codes [B, M*Q] int32 in the per-sample order t0_l0, t0_l1, ..., z_e [B, M, D] fp32)
+        (+ row_max [B] int32, each row's largest id, with return_row_max=True).
+        Eval path encode -> tokenize -> quantize in one engine pass (StepEngine.encode_codes): dropout off whatever
+        self.training says, no EMA update, no re-seeding; codebook, optimizer state and dropout counter are left untouched,
+        and so is a forward / loss_function / backward in flight."""
+        if not self.use_vq or self.quantizer is None:
+            raise _L.VqhError("encode_to_indices: the model has no quantizer (use_vq=False)")
+        eng = self._engine()
+        x, mask = self._prep(x, mask)
+        if x.dim() != 3 or x.shape[2] != 6:
+            raise _L.VqhError(f"encode_to_indices: x must be [B, L, 6], got {tuple(x.shape)}")
+        from vqvae_hip import prior_export as _X
+        B, N, Q = int(x.shape[0]), self.latent_n_tokens, self.quantizer.num_quantizers
+        idx, z_e = eng.encode_codes(x, mask)
+        codes, row_max = _X.pack_codes(idx, Q, B, N)
+        z_e = z_e.view(B, N, self.code_dim).clone()
+        return (codes, z_e, row_max) if return_row_max else (codes, z_e)
+
+    @torch.no_grad()
+    def decode_from_indices(self, codes, target_len=None, mask: Optional[Tensor] = None) -> Tensor:
+        """codes [B, M*Q] (or 1-D [M*Q]) -> recons [B, Lmax, 6]: codebook lookup with the sum over the residual levels, then
+        decode().  target_len: an int, a [B] tensor or a list of per-sample lengths -> a prefix mask padded to the longest
+        one; positions beyond a sample's length are unspecified, as for decode().  The reference's decode_with_vqvae.py probes
+        for this method name and the target_len= keyword."""
+        if not self.use_vq or self.quantizer is None:
+            raise _L.VqhError("decode_from_indices: the model has no quantizer (use_vq=False)")
+        from vqvae_hip import prior_export as _X
+        dev = self.quantizer.embedding.device
+        codes = torch.as_tensor(codes)
+        if codes.dim() == 1:
+            codes = codes.unsqueeze(0)
+        codes = codes.to(dev)
+        B = int(codes.shape[0])
+        if mask is None and target_len is not None:
+            lens = torch.as_tensor(target_len).reshape(-1).to(torch.int64)
+            if lens.numel() == 1:
+                lens = lens.expand(B)
+            if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > self.max_seq_len:
+                raise _L.VqhError(f"decode_from_indices: target_len must give {B} lengths in 1..{self.max_seq_len}")
+            mask = torch.arange(int(lens.max()))[None, :] < lens.cpu()[:, None]
+        if mask is not None:
+            mask = mask.to(device=dev, dtype=torch.bool).contiguous()
+        if codes.dim() != 2 or codes.shape[1] != self.latent_n_tokens * self.quantizer.num_quantizers:
+            raise _L.VqhError(f"decode_from_indices: codes of shape {tuple(codes.shape)}, expected "
+                              f"{self.latent_n_tokens * self.quantizer.num_quantizers} per sample")
+        z_q = _X.codes_to_latent(codes, self.quantizer.embedding, self.quantizer.num_quantizers)
+        return self.decode(z_q, mask=mask)
+
     @torch.no_grad()
     def sample_filtered(self, num_samples: int, device, out_len: Optional[int] = None, params=None, max_rounds: int = 8):
         """sample -> validity screen on the GPU (vqvae_hip.curve_filter, the reference's prior/filter_curves.py rules with

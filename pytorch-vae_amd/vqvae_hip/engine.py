@@ -862,6 +862,56 @@ class StepEngine:
         call("vqh_vq_usage_stats", usage, K, float(Q * R), q._ep_usage, q._ep_cnt, self.vq_stats)
         return z_st, z_q, idx, self.vq_stats
 
+    def encode_codes(self, x, mask):
+        """Eval-mode encode -> tokenize -> nearest codes of every residual level, for the export of prior-training data
+        (the reference's extract_code_indices.py:tokenize_and_quantize with q(z_e, do_ema_update=False, allow_reinit=False,
+        mask=None)).  x [B, L0, 6], mask [B, L0] bool or None -> (idx [Q*B*N] int64 level-major, z_e [B*N, D]), both buffers
+        of the export arena.  Dropout is off whatever the mode, and nothing but the nearest search and the residual is
+        evaluated: no statistics, no EMA refresh, no re-seeding, no epoch accumulators, no decode.  The pass runs in its own
+        arena (at the step's length bucket) and puts the engine's arena, context and mode flags back, so it may run between a
+        forward and its loss_function / backward."""
+        q = self.m.quantizer
+        B, L0 = int(x.shape[0]), int(x.shape[1])
+        Lb = self.bucket_len(L0) if mask is not None else L0
+        prev_key, prev = self.arena.key, (self.train, self.defer_ema, self._pending_ema, self.ctx)
+        self.train, self.ctx = False, {}
+        self.use_arena(("export", B, Lb))
+        try:
+            xt = self.T("in.x", B, Lb, 6)
+            xt[:, :L0].copy_(x, non_blocking=True)
+            ms = None
+            if mask is not None:
+                ms = self.T("in.mask", B, Lb, dtype=torch.bool)
+                ms[:, :L0].copy_(mask, non_blocking=True)
+            if Lb != L0:
+                xt[:, L0:].zero_()
+                ms[:, L0:].fill_(False)
+            hf, _, _ = self.encode(xt, ms)
+            z_e = self.tokenize(hf, ms, B, Lb)
+            D, R = self.D, z_e.shape[0]
+            Q, Kp = q.num_quantizers, q.K_per
+            idx = self.T("vq.idx", Q * R, dtype=torch.int64)
+            res = [self.T("vq.res0", R, D), self.T("vq.res1", R, D)]
+            want = L.vq_nearest_workspace(R, Kp, D)
+            if (want > self.ws.numel() and not torch.cuda.is_current_stream_capturing()
+                    and not any(a.graphs for a in self.arenas.values())):
+                self.ws = torch.empty(want, device=self.dev, dtype=torch.float32)
+            rows = z_e
+            for lv in range(Q):
+                lo = lv * Kp
+                tab = q.embedding[lo:lo + Kp]
+                ids = idx[lv * R:(lv + 1) * R]
+                call("vqh_vq_nearest", rows, D, tab, D, ids, lo, R, Kp, D, 3e-5, self.ws, self.ws.numel())
+                if lv + 1 < Q:
+                    nxt = res[lv & 1]
+                    call("vqh_vq_gather", tab, D, ids, lo, rows, D, None, nxt, R, D)
+                    rows = nxt
+            return idx, z_e
+        finally:
+            self.train, self.defer_ema, self._pending_ema, self.ctx = prev
+            if prev_key in self.arenas:
+                self.use_arena(prev_key)
+
     def maybe_reinit_dead_codes(self):
         """Trigger of VQVAE.forward (models/vq_vae.py:874-891) + VectorQuantizerEMA._maybe_reinit_dead_codes (:91-107).
         Runs eagerly after the step (the step's z_q was gathered before, so only later steps see the new codes).

@@ -60,6 +60,9 @@ _PROTOS = {
     "vqh_grad_norm": "plpppp",
     "vqh_adamw_step": "pppplppp",
     "vqh_curve_filter": "piiipipppppp",
+    "vqh_codes_pack": "piiippp",
+    "vqh_codes_to_latent": "piiipiiippp",
+    "vqh_latent_geometry": "piiipiipp",
 }
 _CT = {"i": C.c_int, "f": C.c_float, "p": C.c_void_p, "l": C.c_longlong, "u": C.c_uint}
 EXPORTS = ["vqh_last_error", "vqh_abi_version", "vqh_gemm_p3_eligible", "vqh_vq_nearest_form", "vqh_vq_nearest_workspace", "vqh_gemm_set_flags", "vqh_attn_set_flags", "vqh_gemm_profile_begin", "vqh_gemm_profile_end",
