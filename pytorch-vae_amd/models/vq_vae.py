@@ -172,22 +172,13 @@ class VectorQuantizerEMA(nn.Module):
         B, M, D = z_e.shape
         eng = self._owner()._engine()
         # a stand-alone call between the model's forward / loss_function / backward must not disturb them: it runs in its
-        # own arena and puts the engine's arena, mode flags and pending-refresh state back afterwards
-        prev_key, prev = eng.arena.key, (eng.train, eng.defer_ema, eng._pending_ema)
-        eng.train = self.training
-        eng.defer_ema = False
-        eng.use_arena(("vq", int(B), int(M)))
-        try:
+        # own arena (StepEngine.side_pass)
+        with eng.side_pass(("vq", int(B), int(M)), train=self.training):
             with torch.no_grad():
                 valid = None if mask is None else mask.to(device=z_e.device, dtype=torch.bool).reshape(B * M)
                 z_st, z_q, idx, stats = eng.quantize(z_e.reshape(B * M, D).contiguous(), B, do_ema_update, row_valid=valid)
             idx_out = idx.view(B, M).clone() if self.num_quantizers == 1 else idx.clone()
-            out = z_st.view(B, M, D).clone(), z_q.view(B, M, D).clone(), idx_out, stats.clone()
-        finally:
-            eng.train, eng.defer_ema, eng._pending_ema = prev
-            if prev_key in eng.arenas:
-                eng.use_arena(prev_key)
-        return out
+            return z_st.view(B, M, D).clone(), z_q.view(B, M, D).clone(), idx_out, stats.clone()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -368,9 +359,8 @@ class VQVAE(nn.Module):
     def encode(self, x, mask=None):
         eng = self._engine()
         x, mask = self._prep(x, mask)
-        eng.train, eng.ctx = self.training, {}
         B, Lq, _ = x.shape
-        eng.use_arena((int(B), int(Lq)))
+        eng.begin(B, Lq, self.training, fresh_ctx=True)
         hf, hg, hs = eng.encode(x, mask)
         H = self.hidden_dim
         return hf.view(B, Lq, H).clone(), hg.view(B, Lq, H).clone(), hs.view(B, Lq, H).clone()
@@ -379,10 +369,7 @@ class VQVAE(nn.Module):
     def _tokenize_to_codes(self, h_tokens: Tensor, mask: Optional[Tensor]) -> Tensor:
         eng = self._engine()
         B, Lq, H = h_tokens.shape
-        eng.train = self.training
-        eng.use_arena((int(B), int(Lq)))
-        if eng.ctx is None:
-            eng.ctx = {}
+        eng.begin(B, Lq, self.training)
         eng.ctx.update({"B": B, "L": Lq, "mask": mask})
         hf = eng.T("fuse.out", B * Lq, H)
         hf.copy_(h_tokens.reshape(B * Lq, H))
@@ -394,10 +381,7 @@ class VQVAE(nn.Module):
         eng = self._engine()
         B = z_for_decode.shape[0]
         Lq = mask.shape[1] if mask is not None else self.max_seq_len
-        eng.train = self.training
-        eng.use_arena((int(B), int(Lq)))
-        if eng.ctx is None:
-            eng.ctx = {}
+        eng.begin(B, Lq, self.training)
         z = z_for_decode.reshape(-1, self.code_dim).contiguous().float()
         rec = eng.decode(z, mask.contiguous() if mask is not None else None, B, Lq)
         return rec.view(B, Lq, 6).clone()
@@ -410,6 +394,7 @@ class VQVAE(nn.Module):
         N, D = self.latent_n_tokens, self.code_dim
         if self.use_vq:
             idx_out = idx.view(B, N) if self.num_quantizers == 1 else idx
+            stats = stats.clone()                  # the engine's pair is rewritten by the next quantizer call, also a stand-alone one
             ppl, dead = stats[0], stats[1]
         else:
             idx_out = torch.zeros(B, N, dtype=torch.long, device=x.device)

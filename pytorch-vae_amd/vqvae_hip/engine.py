@@ -19,6 +19,7 @@ Memory layout in HBM (all fp32, row-major):
   * residual-stream gradient: one [rows, H] buffer per stack, updated in place layer by layer
 """
 import collections
+import contextlib
 import gc
 import os
 import weakref
@@ -174,19 +175,6 @@ class StepEngine:
         self.group_wgrad = os.environ.get("VQH_GROUP_WGRAD", "1") != "0"
         self._wq = []
         self._dy_slot = 0
-        # EXPERIMENT, off by default (VQH_OVERLAP_WGRAD=1): the grouped weight-gradient launch of a layer on a SECOND stream
-        # while the main stream goes on with the next layer's backward (nothing reads a weight gradient before the clip), so
-        # that the prologue / epilogue / drain gaps of one kernel are filled with workgroups of the other.  Measured on C2:
-        # 27.04 ms per step against 26.64 ms in order -- both kernels want a whole CU's LDS, so they only alternate, and two
-        # operand working sets share each XCD's L2.  Results are identical (same kernels, same order per gradient).
-        # Single process only: with several ranks a phase's gradients must be final at its bucket's all-reduce, and a graph
-        # segment has to rejoin its forked streams.
-        self.overlap_wgrad = self.group_wgrad and os.environ.get("VQH_OVERLAP_WGRAD", "0") == "1"
-        self._side = None                     # the second stream
-        self._ws_side = None                  # its own split-K workspace
-        self._side_busy = False
-        self._par = 0                         # parity of the operand buffers handed out by TW()
-        self._buf_ev = {}                     # storage pointer of an operand buffer -> event of the side launch that reads it
 
     @property
     def m(self):
@@ -264,16 +252,40 @@ class StepEngine:
     def bucket_len(self, L0):
         return bucket_length(L0, self.len_bucket, self.m.max_seq_len)
 
-    def _stage_batch(self, x, mask):
+    def begin(self, B, Lq, train, fresh_ctx=False):
+        """Open a stand-alone model section (VQVAE.encode / _tokenize_to_codes / decode) in the step's own arena (B, Lq):
+        these are no side passes, they continue (or, fresh_ctx, start) the context a later section reads."""
+        self.train = bool(train)
+        self.use_arena((int(B), int(Lq)))
+        if fresh_ctx or self.ctx is None:
+            self.ctx = {}
+
+    @contextlib.contextmanager
+    def side_pass(self, key, train=False):
+        """An inference pass next to a step in flight: runs in the arena `key` of its own with a fresh context and no
+        deferred EMA refresh, and puts the arena, train, defer_ema, _pending_ema and ctx back on exit (also on an exception),
+        so it may run between a forward and its loss_function / backward."""
+        prev_key, prev = self.arena.key, (self.train, self.defer_ema, self._pending_ema, self.ctx)
+        self.train, self.defer_ema, self.ctx = bool(train), False, {}
+        self.use_arena(key)
+        try:
+            yield self
+        finally:
+            self.train, self.defer_ema, self._pending_ema, self.ctx = prev
+            if prev_key in self.arenas:
+                self.use_arena(prev_key)
+
+    def _stage_batch(self, x, mask, key=None):
         """Copy the batch into the bucketed input buffers of the current shape's arena (outside any graph): x [B, L0, 6] ->
         in.x [B, Lb, 6] zero padded, mask -> in.mask [B, Lb] with False on the padded tail.  x / mask may live on the host:
         a pinned batch (DataLoader pin_memory) then goes host -> arena in ONE asynchronous copy, queued behind the previous
         step's graph on the same stream (C2: 0.4 MB, ~10 us) -- there is no intermediate device tensor.  Returns (arena, x, mask); the
-        mask stays None when the caller passed none and nothing was padded (the reference's mask=None variant)."""
+        mask stays None when the caller passed none and nothing was padded (the reference's mask=None variant).  The arena
+        is (B, Lb) unless the caller names one (`key`: a side pass stages into its own)."""
         B, L0 = int(x.shape[0]), int(x.shape[1])
         # mask=None is the reference's un-masked variant (different normalisers): such a batch keeps its own length
         Lb = self.bucket_len(L0) if mask is not None else L0
-        a = self.use_arena((B, Lb))
+        a = self.use_arena((B, Lb) if key is None else key)
         xt = self.T("in.x", B, Lb, int(x.shape[2]))
         if Lb == L0:
             xt.copy_(x, non_blocking=True)
@@ -354,42 +366,14 @@ class StepEngine:
 
     def flush_wgrads(self):
         """Run the queued weight-gradient products of the layer just finished as one grouped launch."""
-        if self._wq:
-            from .parallel import dp_active
-            if self.overlap_wgrad and not dp_active():
-                main = torch.cuda.current_stream()
-                if self._side is None:
-                    self._side = torch.cuda.Stream(device=self.dev)
-                    self._ws_side = torch.empty(WS_FLOATS, device=self.dev, dtype=torch.float32)
-                self._side.wait_stream(main)              # operands and the gradients' earlier contents are ordered before it
-                with torch.cuda.stream(self._side):
-                    L.wgrad_group(self._wq, self._ws_side)
-                ev = torch.cuda.Event()
-                ev.record(self._side)
-                for it in self._wq:                       # whoever rewrites an operand buffer waits for this launch (TW)
-                    self._buf_ev[it[0].untyped_storage().data_ptr()] = ev
-                self._side_busy = True
-            else:
-                L.wgrad_group(self._wq, self.ws)
-            self._wq = []
+        L.wgrad_group(self._wq, self.ws)                  # no launch for an empty queue
+        self._wq = []
         self._dy_slot = 0
-        self._par ^= 1
-
-    def join_wgrads(self):
-        """The main stream waits for every weight-gradient launch of the second stream (before anything reads a gradient)."""
-        if self._side_busy:
-            torch.cuda.current_stream().wait_stream(self._side)
-            self._side_busy = False
-        self._buf_ev.clear()
 
     def TW(self, name, *shape):
-        """A scratch buffer that a DEFERRED weight-gradient product will read (its dY operand): two copies alternate from layer
-        to layer, and a copy is handed out again only after the launch that read it (recorded in flush_wgrads)."""
-        t = self.T(f"{name}@{self._par}" if self.overlap_wgrad else name, *shape)
-        ev = self._buf_ev.pop(t.untyped_storage().data_ptr(), None)
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
-        return t
+        """A scratch buffer that a DEFERRED weight-gradient product reads (its dY operand) until the layer's flush_wgrads():
+        it must not be rewritten before then."""
+        return self.T(name, *shape)
 
     def dy_tag(self):
         """Name of a fresh buffer for a block's output gradient (valid until the next flush_wgrads)."""
@@ -660,17 +644,13 @@ class StepEngine:
         dy0 = self.ln_bwd("enc_ln", dhg, H, xs[-1], H, "enc_ln", dres, H, False, ML,
                           emit=(self.site(f"encoder.layers.{nl - 1}.linear2.drop"), self.pdrop(0.1), "tmp.dy_carry_in")
                           if nl > 0 else None)
-        embed_done = False
         for i in self._encoder_stack_bwd("encoder", nl, xs, dres, ML, B, Lq, mask, dy0=dy0):
-            if i == 0:                                # input_proj belongs to the last phase
-                call("vqh_embed_bwd", dres, c["x"], 6, 0, self.G["input_proj.weight"], self.G["input_proj.bias"], 0.0, ML, H,
-                     self.rng, self.site("inp_dropout"), self.pdrop(0.1), self.ws, self.ws.numel())
-                embed_done = True
-            yield i
-        if not embed_done:                            # num_layers == 0
-            call("vqh_embed_bwd", dres, c["x"], 6, 0, self.G["input_proj.weight"], self.G["input_proj.bias"], 0.0, ML, H,
-                 self.rng, self.site("inp_dropout"), self.pdrop(0.1), self.ws, self.ws.numel())
-            yield 0
+            if i > 0:
+                yield i
+        # input_proj belongs to the last phase: behind layer 0, or on its own when num_layers == 0
+        call("vqh_embed_bwd", dres, c["x"], 6, 0, self.G["input_proj.weight"], self.G["input_proj.bias"], 0.0, ML, H,
+             self.rng, self.site("inp_dropout"), self.pdrop(0.1), self.ws, self.ws.numel())
+        yield 0
 
     def tokenize(self, hf, mask, B, Lq):
         """LatentTokenizer + to_code (models/vq_vae.py:310-322, 736-743) -> z_e [B*N, D]"""
@@ -760,19 +740,40 @@ class StepEngine:
         alpha = 1.0 if aw <= 0 else min(1.0, float(m.training_steps) / float(aw))
         return float(tau), float(alpha)
 
-    def _soft_vq_key(self):
-        p = self._soft_vq_params() if self.m.use_vq else None
-        return p
-
     def quantize(self, z_e, B, do_ema_update, row_valid=None):
         """quantize_gen driven to completion, with the per-level statistics all-reduce done inline (eager callers)."""
-        gen = self.quantize_gen(z_e, B, do_ema_update, row_valid)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as stop:
-                return stop.value
-            torch.distributed.all_reduce(self.flat_gx[self.n_flat:])      # RCCL sum of the EMA statistics over ranks
+        return self._drive(self.quantize_gen(z_e, B, do_ema_update, row_valid))
+
+    def _vq_workspace(self, R, Kp, D):
+        """The plane-tensor score form of vqh_vq_nearest wants room for the split Z / codebook images: grow the workspace
+        to it, but only while no captured graph holds its address (eager steps come first)."""
+        want = L.vq_nearest_workspace(R, Kp, D)
+        if (want > self.ws.numel() and not torch.cuda.is_current_stream_capturing()
+                and not any(a.graphs for a in self.arenas.values())):
+            self.ws = torch.empty(want, device=self.dev, dtype=torch.float32)
+
+    def _residual_levels(self, z_e, idx, zq_lv=None):
+        """Generator over the residual quantizer levels: nearest code of the current residual into idx's slice of the level,
+        then the gather that leaves the next level's residual (and z_q of this level in zq_lv[lv] when given; without a
+        zq_lv it only runs while a next level exists).  Yields (lv, lo, ids, rows) with rows = the level's input; the caller's
+        loop body (statistics, EMA refresh) runs behind the gather and before the next level's search."""
+        q = self.m.quantizer
+        D, R = self.D, z_e.shape[0]
+        Q, Kp = q.num_quantizers, q.K_per
+        res = [self.T("vq.res0", R, D), self.T("vq.res1", R, D)]
+        self._vq_workspace(R, Kp, D)
+        rows = z_e
+        for lv in range(Q):
+            lo = lv * Kp
+            tab = q.embedding[lo:lo + Kp]
+            ids = idx[lv * R:(lv + 1) * R]
+            call("vqh_vq_nearest", rows, D, tab, D, ids, lo, R, Kp, D, 3e-5, self.ws, self.ws.numel())
+            nxt = res[lv & 1] if lv + 1 < Q else None
+            if zq_lv is not None or nxt is not None:
+                # gather uses the table BEFORE this level's EMA refresh (:189 precedes :191-197 / :248 precedes :251-258)
+                call("vqh_vq_gather", tab, D, ids, lo, rows, D, None if zq_lv is None else zq_lv[lv], nxt, R, D)
+            yield lv, lo, ids, rows
+            rows = nxt
 
     def quantize_gen(self, z_e, B, do_ema_update, row_valid=None):
         """Generator form: yields where the EMA statistics [cnt | sum] of a level must be summed over the ranks BEFORE that
@@ -800,22 +801,7 @@ class StepEngine:
                 upd = False
         from .parallel import dp_active
         multi = dp_active()
-        rows = z_e
-        res = [self.T("vq.res0", R, D), self.T("vq.res1", R, D)]
-        # the plane-tensor score form wants room for the split Z / codebook images; the workspace can only move while no
-        # captured graph holds its address (eager steps come first)
-        want = L.vq_nearest_workspace(R, Kp, D)
-        if (want > self.ws.numel() and not torch.cuda.is_current_stream_capturing()
-                and not any(a.graphs for a in self.arenas.values())):
-            self.ws = torch.empty(want, device=self.dev, dtype=torch.float32)
-        for lv in range(Q):
-            lo = lv * Kp
-            tab = emb[lo:lo + Kp]
-            ids = idx[lv * R:(lv + 1) * R]
-            call("vqh_vq_nearest", rows, D, tab, D, ids, lo, R, Kp, D, 3e-5, self.ws, self.ws.numel())
-            nxt = res[lv & 1] if lv + 1 < Q else None
-            # gather uses the table BEFORE this level's EMA refresh (:189 precedes :191-197 / :248 precedes :251-258)
-            call("vqh_vq_gather", tab, D, ids, lo, rows, D, zq_lv[lv], nxt, R, D)
+        for lv, lo, ids, rows in self._residual_levels(z_e, idx, zq_lv):
             # per-code statistics of THIS level (other code ranges stay zero: the reference refreshes the whole table)
             call("vqh_memset", cnt, 0, K * 4)
             call("vqh_memset", ssum, 0, K * D * 4)
@@ -837,9 +823,8 @@ class StepEngine:
                 self._pending_ema = float(q.decay)
             elif upd:
                 if multi:                                   # RCCL sum of the EMA statistics over ranks
-                    yield "stats"
+                    yield ("stats",)
                 self.apply_ema(float(q.decay))
-            rows = nxt
         z_q, z_st = self.T("vq.z_q", R, D), self.T("vq.z_st", R, D)
         call("vqh_vq_finish", zq_lv, Q, z_e, D, z_q, z_st, R, D)
         soft = self._soft_vq_params()
@@ -870,47 +855,16 @@ class StepEngine:
         evaluated: no statistics, no EMA refresh, no re-seeding, no epoch accumulators, no decode.  The pass runs in its own
         arena (at the step's length bucket) and puts the engine's arena, context and mode flags back, so it may run between a
         forward and its loss_function / backward."""
-        q = self.m.quantizer
         B, L0 = int(x.shape[0]), int(x.shape[1])
-        Lb = self.bucket_len(L0) if mask is not None else L0
-        prev_key, prev = self.arena.key, (self.train, self.defer_ema, self._pending_ema, self.ctx)
-        self.train, self.ctx = False, {}
-        self.use_arena(("export", B, Lb))
-        try:
-            xt = self.T("in.x", B, Lb, 6)
-            xt[:, :L0].copy_(x, non_blocking=True)
-            ms = None
-            if mask is not None:
-                ms = self.T("in.mask", B, Lb, dtype=torch.bool)
-                ms[:, :L0].copy_(mask, non_blocking=True)
-            if Lb != L0:
-                xt[:, L0:].zero_()
-                ms[:, L0:].fill_(False)
+        key = ("export", B, self.bucket_len(L0) if mask is not None else L0)
+        with self.side_pass(key):
+            _, xt, ms = self._stage_batch(x, mask, key)
             hf, _, _ = self.encode(xt, ms)
-            z_e = self.tokenize(hf, ms, B, Lb)
-            D, R = self.D, z_e.shape[0]
-            Q, Kp = q.num_quantizers, q.K_per
-            idx = self.T("vq.idx", Q * R, dtype=torch.int64)
-            res = [self.T("vq.res0", R, D), self.T("vq.res1", R, D)]
-            want = L.vq_nearest_workspace(R, Kp, D)
-            if (want > self.ws.numel() and not torch.cuda.is_current_stream_capturing()
-                    and not any(a.graphs for a in self.arenas.values())):
-                self.ws = torch.empty(want, device=self.dev, dtype=torch.float32)
-            rows = z_e
-            for lv in range(Q):
-                lo = lv * Kp
-                tab = q.embedding[lo:lo + Kp]
-                ids = idx[lv * R:(lv + 1) * R]
-                call("vqh_vq_nearest", rows, D, tab, D, ids, lo, R, Kp, D, 3e-5, self.ws, self.ws.numel())
-                if lv + 1 < Q:
-                    nxt = res[lv & 1]
-                    call("vqh_vq_gather", tab, D, ids, lo, rows, D, None, nxt, R, D)
-                    rows = nxt
+            z_e = self.tokenize(hf, ms, B, key[2])
+            idx = self.T("vq.idx", self.m.quantizer.num_quantizers * z_e.shape[0], dtype=torch.int64)
+            for _ in self._residual_levels(z_e, idx):
+                pass
             return idx, z_e
-        finally:
-            self.train, self.defer_ema, self._pending_ema, self.ctx = prev
-            if prev_key in self.arenas:
-                self.use_arena(prev_key)
 
     def maybe_reinit_dead_codes(self):
         """Trigger of VQVAE.forward (models/vq_vae.py:874-891) + VectorQuantizerEMA._maybe_reinit_dead_codes (:91-107).
@@ -1092,13 +1046,7 @@ class StepEngine:
         return bool(self.train and m.use_vq and (m.training_steps >= m.ema_update_freeze_steps))
 
     def _forward_core(self, x, mask, upd):
-        gen = self._forward_core_gen(x, mask, upd)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as stop:
-                return stop.value
-            torch.distributed.all_reduce(self.flat_gx[self.n_flat:])
+        return self._drive(self._forward_core_gen(x, mask, upd))
 
     def _forward_core_gen(self, x, mask, upd):
         m = self.m
@@ -1178,7 +1126,6 @@ class StepEngine:
         """Backward as a generator over the phases of bwd_phases(): after the k-th yield, bucket self.buckets[k] of the flat
         gradient is final (its all-reduce may start)."""
         c = self.ctx
-        self._par = 0                                   # the same buffer names in every backward (graphs replay their own)
         for _ in self.decode_bwd_gen(c["d_rec"], c["d_ze"], 1.0 if self.m.use_vq else 0.0):
             yield
         c["d_hf"] = self.tokenize_bwd(c["d_ze"])
@@ -1189,7 +1136,6 @@ class StepEngine:
         yield
         for _ in self.encode_bwd_geo():
             yield
-        self.join_wgrads()
 
     def set_hyper(self, lr, weight_decay, max_norm, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, L_logical=0):
         """Host -> device scalars of the next optimizer step (copied on the current stream, outside any graph)."""
@@ -1250,14 +1196,7 @@ class StepEngine:
         A single process ignores the yields (one graph holds everything); with several ranks the stretches between two
         yields become separate hipGraph segments and the collectives run between their replays (StepEngine._replay)."""
         self.advance_rng()
-        fwd = self._forward_core_gen(x_in, mask, upd)
-        while True:
-            try:
-                next(fwd)
-            except StopIteration as stop:
-                rec, z_e, z_q, idx, stats = stop.value
-                break
-            yield ("stats",)
+        rec, z_e, z_q, idx, stats = yield from self._forward_core_gen(x_in, mask, upd)
         self.loss(rec, x_tgt, mask, z_e, z_q, stats, weights, L_dev=self.hyper[9:])   # L_max of THIS batch: set_hyper
         ph = 0
         for _ in self.backward_gen():
@@ -1277,11 +1216,20 @@ class StepEngine:
                 w.wait()
             del works[:]
 
-    def _step_eager(self, x_in, x_tgt, mask, weights, upd, dp):
+    def _drive(self, gen, act=True):
+        """Run a generator of the step protocol (_step_gen's yields) to its return value, performing the collective of every
+        yield -- or none of them (act False: a single process, where the yields mean nothing)."""
         works = []
-        for action in self._step_gen(x_in, x_tgt, mask, weights, upd):
-            if dp:
+        while True:
+            try:
+                action = next(gen)
+            except StopIteration as stop:
+                return stop.value
+            if act:
                 self._act(action, works)
+
+    def _step_eager(self, x_in, x_tgt, mask, weights, upd, dp):
+        self._drive(self._step_gen(x_in, x_tgt, mask, weights, upd), act=dp)
 
     def _step_part_b(self):
         self.finish_ema()
@@ -1329,7 +1277,7 @@ class StepEngine:
         # everything a captured graph bakes in as a kernel argument (the batch shape is the arena)
         key = (ms is not None, tuple(sorted((k, float(v)) for k, v in weights.items())), upd, decay,
                world, dp, self.drop_scale, float(m.quantizer.beta) if m.use_vq else 0.0, float(m.label_smoothing or 0.0),
-               x_in is xt, float(m.usage_entropy_lambda), self._soft_vq_key(), self.share_layer0, self.fold_dropout_bwd, self.group_wgrad,
+               x_in is xt, float(m.usage_entropy_lambda), self._soft_vq_params(), self.share_layer0, self.fold_dropout_bwd, self.group_wgrad,
                float(m.xyz_align_alpha), float(m.ss_tv_lambda), m._data_std is not None)
         xs = x_in
         use_graph = bool(use_graph) and os.environ.get("VQH_GRAPH", "1") != "0"

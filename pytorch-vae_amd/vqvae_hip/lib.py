@@ -6,6 +6,7 @@ called, callers get a loud VqhError.  PyTorch is used only for device memory (te
 HIP stream and torch.distributed; every arithmetic kernel of the training step lives in the library."""
 import ctypes as C
 import os
+import sys
 
 import torch
 
@@ -103,7 +104,6 @@ def lib():
                     raise VqhError(f"{env}={val}: bits {val & bad} are result-corrupting timing diagnostics, not available "
                                    f"in the product library")
                 getattr(L, setter)(val)
-                import sys
                 print(f"[vqvae_hip] {env}={val} applied ({setter}): kernel A/B override for this process", file=sys.stderr)
         _lib = L
     return _lib
@@ -145,7 +145,9 @@ EPI_LINEAR, EPI_RELU_DROP, EPI_GELU, EPI_DROP_RESID, EPI_SIGMOID, EPI_MUL_POSMAS
 
 def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, Cout, ldc, bias=None, mode=EPI_LINEAR, aux_in=None, aux_out=None,
          ldaux=0, beta=0.0, rng=None, site=0, p=0.0, ws=None):
-    _gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, Cout, ldc, bias, mode, aux_in, aux_out, ldaux, beta, rng, site, p, ws)
+    call("vqh_gemm", int(a_kc), int(b_kc), M, N, K, _p(A), lda, _p(B), ldb, _p(Cout), ldc, _p(bias), mode,
+         _p(aux_in), _p(aux_out), ldaux, float(beta), _p(rng), site, float(p), _p(ws),
+         (ws.numel() if ws is not None else 0))
 
 
 GEMM_PROF_FAMILIES = 7
@@ -158,14 +160,13 @@ def gemm_profile(fn):
     family 1 = gemm_f32_dma<a_kc, b_kc, MODE> (256x128 tile, LDS-DMA, native fp32 MFMA), family 2 = gemm_f32_dma_group (grouped
     weight gradients), families 3 / 4 = gemm_f32_x3<...> / gemm_f32_x3_group: the same tiles on the bf16 matrix pipes (exact 3-way
     operand split, 6 products; the default)."""
-    import ctypes
     lib().vqh_gemm_profile_begin()
     try:
         fn()
         torch.cuda.synchronize()
     finally:
-        out = (ctypes.c_double * (GEMM_PROF_FAMILIES * 4 * 9 * 3))()
-        rc = lib().vqh_gemm_profile_end(ctypes.cast(out, ctypes.c_void_p))
+        out = (C.c_double * (GEMM_PROF_FAMILIES * 4 * 9 * 3))()
+        rc = lib().vqh_gemm_profile_end(C.cast(out, C.c_void_p))
     if rc != 0:
         raise VqhError(f"vqh_gemm_profile_end failed: {lib().vqh_last_error().decode()}")
     res = {}
@@ -181,14 +182,13 @@ def gemm_profile(fn):
 
 def vq_profile(fn):
     """Run fn() with per-launch timing of the nearest-neighbour main kernel on; returns (launches, seconds, flops)."""
-    import ctypes
     lib().vqh_vq_profile_begin()
     try:
         fn()
         torch.cuda.synchronize()
     finally:
-        out = (ctypes.c_double * 3)()
-        rc = lib().vqh_vq_profile_end(ctypes.cast(out, ctypes.c_void_p))
+        out = (C.c_double * 3)()
+        rc = lib().vqh_vq_profile_end(C.cast(out, C.c_void_p))
     if rc != 0:
         raise VqhError(f"vqh_vq_profile_end failed: {lib().vqh_last_error().decode()}")
     return int(out[0]), out[1], out[2]
@@ -229,12 +229,6 @@ def wgrad_group(items, ws):
         arr[i] = WgradT(int(rows), int(n_out), int(k_in), dy.data_ptr(), int(lddy), x.data_ptr(), int(ldx), gW.data_ptr(),
                         int(gW.stride(0)), _p(gb))
     call("vqh_gemm_wgrad_group", n, C.cast(arr, C.c_void_p), ws, ws.numel())
-
-
-def _gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, Cout, ldc, bias, mode, aux_in, aux_out, ldaux, beta, rng, site, p, ws):
-    call("vqh_gemm", int(a_kc), int(b_kc), M, N, K, _p(A), lda, _p(B), ldb, _p(Cout), ldc, _p(bias), mode,
-         _p(aux_in), _p(aux_out), ldaux, float(beta), _p(rng), site, float(p), _p(ws),
-         (ws.numel() if ws is not None else 0))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
